@@ -23,11 +23,23 @@ RCCL all-to-all, untimed setup).  Strong scaling: the total work is the same
 at every N.  `value` = edges traversed by the whole search / max-over-ranks
 time.  `--sharded` takes the sharded path at N = 1 (rehearsal).
 
+A plain run sets up, warms up, times the steps, writes its outputs when
+`--dump-outputs DIR` is given and prints the JSON line.  Everything else is
+behind `--full`:
+
 Parity: after the timed steps the same search is run once more with result
 files and compared with the oracle's S=28 digest (tests/golden/
 rmat_s28_p8_tree.json, made by tests/golden/make_rmat_fixture.py); the CPU
 baseline leg runs the oracle on a bounded S=24 sample and the GPU on the same
 sample, and compares their counters.  A mismatch prints "invalid" and exits 3.
+`--full` also times configs C3 and C5 and the sharded path at N = 1 and
+measures the device's copy bandwidth for the roofline.
+
+`--dump-outputs DIR`: the state the last timed search left in its context (what
+PatternMatcher.export_state() returns to a caller: the vertices of S, their
+template bits and active degrees, the active neighbour lists) and its counters,
+as DIR/<name>.npy.  The graph and labels are generated from fixed seeds, so two
+builds given the same arguments write comparable files.
 """
 import argparse
 import json
@@ -116,6 +128,36 @@ def line_stream():
     return os.fdopen(fd, "w")
 
 
+DUMP_MAX_ENTRIES = 1 << 20  # per array (float64: 8 MiB; five arrays stay far below 64 MB)
+DUMP_COUNTERS = ("iterations", "terminated", "final_vertices", "final_edges", "lcc_edges", "nlcc_edges", "tds_edges",
+                 "walks")
+
+
+def dump_sample(a):
+    """`a` itself, or a fixed (seeded) sorted sample of DUMP_MAX_ENTRIES of its entries."""
+    import numpy as np
+    if a.shape[0] <= DUMP_MAX_ENTRIES:
+        return a
+    return a[np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ENTRIES, replace=False))]
+
+
+def dump_outputs(out_dir, state, last):
+    """The last timed search's result as <out_dir>/<name>.npy: `state` = export_state() of its context, `last` its
+    counters.  Ids, degrees and counters as float64 (exact below 2^53), the u16 template bits as float32."""
+    import numpy as np
+    tpub, mdeg, nbrs = state
+    ids = np.flatnonzero(tpub)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"vertices": dump_sample(ids).astype(np.float64),
+              "template_bits": dump_sample(tpub[ids]).astype(np.float32),
+              "active_degree": dump_sample(mdeg[ids]).astype(np.float64),
+              "active_neighbours": dump_sample(nbrs).astype(np.float64),
+              "counters": np.array([last[k] for k in DUMP_COUNTERS], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: int(a.shape[0]) for name, a in arrays.items()}
+
+
 def spread(vals):
     vals = [float(v) for v in vals]
     mean = sum(vals) / len(vals) if vals else 0.0
@@ -135,10 +177,17 @@ def main():
     ap.add_argument("--pattern", default="rmat_log2_tree_pattern")
     ap.add_argument("--max-iterations", type=int, default=64)
     ap.add_argument("--hub-threshold", type=int, default=1048576, help="-d of generate_rmat (delegates)")
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every leg whose option below is `auto`: the CPU baselines, the "
+                         "oracle fixture checks, configs C3 and C5, the sharded path at N=1 and the copy-bandwidth "
+                         "measurement of the roofline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the final state of the search and its counters) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto", help="auto: with --full")
     ap.add_argument("--cpu-scale", type=int, default=24,
                     help="the CPU baseline runs the same search at min(scale, cpu-scale) (bounded sample)")
-    ap.add_argument("--fixture-check", choices=["auto", "off"], default="auto")
+    ap.add_argument("--fixture-check", choices=["auto", "off"], default="auto", help="auto: with --full")
     ap.add_argument("--graph-cache", default=os.environ.get("PM_GRAPH_CACHE"),
                     help="directory: reuse / store the generated one-GPU graph (repeated profiling runs)")
     ap.add_argument("--gen", choices=["gpu", "host"], default="gpu",
@@ -147,15 +196,19 @@ def main():
                     help="take the sharded (RCCL) path even at N=1 (rehearsal of the multi-GPU code on one GPU)")
     ap.add_argument("--pmc", default=None, help="PMC summary of k_lcc_first (default: the newest profiles/r*_pmc_lcc_first.json)")
     ap.add_argument("--c3", choices=["auto", "off"], default="auto",
-                    help="also time BASELINE config C3 (S=26, P_gen=4, 4-cycle: the token-passing stress) at N=1")
+                    help="with --full also time BASELINE config C3 (S=26, P_gen=4, 4-cycle: the token-passing stress) at N=1")
     ap.add_argument("--sharded-n1", choices=["auto", "off"], default="auto",
-                    help="at N=1 also time the sharded path with one shard (one-rank RCCL communicator, the code every "
+                    help="with --full, at N=1 also time the sharded path with one shard (one-rank RCCL communicator, the code every "
                          "rank of an N-GPU run executes) on the same search")
     ap.add_argument("--nlcc", choices=["auto", "off"], default="auto",
-                    help="also time the token-passing path with real work at N=1: config C5's search (S=27, "
-                         "hash32(v ^ 5) % 256 labels, 4-cycle) on the GPU-generated graph, checked against "
+                    help="with --full also time the token-passing path with real work at N=1: config C5's search (S=27, "
+                         "hash32(v ^ 5) %% 256 labels, 4-cycle) on the GPU-generated graph, checked against "
                          "tests/golden/rmat_s27_p8_cycle4_hash256.json")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline figure only
+        args.cpu_baseline = args.fixture_check = args.c3 = args.sharded_n1 = args.nlcc = "off"
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -249,6 +302,14 @@ def main():
         f"final |S|={s0['final_vertices']} |M|={s0['final_edges']}, host {s0['seconds'] * 1e3:.3f} ms, "
         f"device {s0['device_seconds'] * 1e3:.3f} ms, lcc_first kernel {kern_ms:.4f} ms")
 
+    dumped = None
+    if args.dump_outputs:
+        state = m.export_state()  # collective over the shards; every shard holds the whole state
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, state, s0)
+            log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
+        del state
+
     # parity of this very context at the headline size: the oracle's S=28 digest
     invalid = []
     fixture = None
@@ -327,7 +388,7 @@ def main():
     from fuzzypatternmatching_amd import _abi
     copy = ctypes.c_double()
     copy_gbs = None
-    if _abi.load().pm_debug_copy_gbs(local_rank, 4 << 30, 20, ctypes.byref(copy)) == 0:
+    if args.full and _abi.load().pm_debug_copy_gbs(local_rank, 4 << 30, 20, ctypes.byref(copy)) == 0:
         copy_gbs = round(copy.value, 1)
     roofline = {"bound": "hbm", "kernel": "k_lcc_first", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
@@ -540,6 +601,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "strong",
@@ -561,6 +623,7 @@ def main():
         "nlcc_config": nlcc,
         "shards": shards,
         "sharded_n1": sharded1,
+        "dumped_outputs": dumped,
         # one-time work outside the timed region (the reference's graph load + label init analogue)
         "setup_s": setup,
     }

@@ -11,7 +11,7 @@ of the active vertex / edge / subgraph files; run_pattern_matching_beta.cpp:1370
 counters and timings.  The graph comes from the GPU generator (pm_rmat.hip, bit-identical to the
 oracle's own generator: tests/test_gpu_rmat.py), copied to the host; at S=28 the oracle needs
 about 100 GB of host memory, so this runs on the GPU box, once.  The committed fixture is
-tests/golden/rmat_s<S>_p<P>_<pattern>.json; tests/test_gpu_configs.py and bench.py check the
+tests/golden/rmat_s<S>_p<P>_<pattern>.json; tests/test_gpu_configs.py and bench.py --full check the
 GPU search against it.
 """
 import argparse

@@ -165,3 +165,29 @@ def test_bench_refuses_world_size_mismatch():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], capture_output=True,
                        text=True, env=env, timeout=300)
     assert r.returncode == 2 and "WORLD_SIZE=2 but --gpus 4" in r.stderr and r.stdout.strip() == ""
+
+
+def test_bench_dump_outputs_arrays(tmp_path):
+    """--dump-outputs: the arrays of a state (tpub, mdeg, nbrs) -- the members of S only, float32/float64, an
+    oversized array cut to the same seeded sample on every call."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    n = 1 << 12
+    tpub = np.zeros(n, np.uint16)
+    mdeg = np.zeros(n, np.uint32)
+    tpub[[3, 70, 4095]] = [1, 6, 65535]
+    mdeg[[3, 70, 4095]] = [2, 1, 4]
+    nbrs = np.arange(bench.DUMP_MAX_ENTRIES + 5, dtype=np.uint32)
+    last = {k: i for i, k in enumerate(bench.DUMP_COUNTERS)}
+    sizes = [bench.dump_outputs(str(tmp_path / d), (tpub, mdeg, nbrs), last) for d in ("a", "b")]
+    assert sizes[0] == sizes[1] and sizes[0]["active_neighbours"] == bench.DUMP_MAX_ENTRIES
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"vertices", "template_bits", "active_degree", "active_neighbours", "counters"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["vertices"].tolist() == [3, 70, 4095] and got["template_bits"].tolist() == [1, 6, 65535]
+    assert got["active_degree"].tolist() == [2, 1, 4] and got["counters"].tolist() == list(range(len(last)))
+    assert np.all(np.diff(got["active_neighbours"]) > 0)
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20

@@ -10,11 +10,13 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-r06}
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err \
-  || { tail -5 gpurun_out/bench_${TAG}.err; exit 1; }
-tail -4 gpurun_out/bench_${TAG}.err
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_${TAG}.json" 2> "$OUT/bench_${TAG}.err" \
+  || { tail -5 "$OUT/bench_${TAG}.err"; exit 1; }
+tail -4 "$OUT/bench_${TAG}.err"
 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus 1 --sharded --steps 20 --warmup 5 --cpu-baseline off --c3 off --nlcc off --sharded-n1 off \
+    --master-port 29533 bench.py --gpus 1 --sharded --full --steps 20 --warmup 5 --cpu-baseline off --c3 off --nlcc off --sharded-n1 off \
     > gpurun_out/bench_${TAG}_sharded.json 2> gpurun_out/bench_${TAG}_sharded.err \
   || { tail -5 gpurun_out/bench_${TAG}_sharded.err; exit 1; }
 tail -2 gpurun_out/bench_${TAG}_sharded.err
