@@ -201,25 +201,14 @@ def comm_unique_id():
 
 def run_beta_local_shards(graph, pattern_dir, nshards, result_dir="", max_iterations=0, device=0, labels=None):
     """The sharded search with `nshards` shards driven by threads of this process on one
-    device (in-process exchange instead of RCCL): parity of the sharded path on one GPU."""
-    desc = _abi.GraphDesc(graph.n, graph.off.ctypes.data, graph.col.ctypes.data, int(graph.symmetric), graph.nranks,
-                          graph.hub_threshold)
-    lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.uint64)
-    if result_dir:
-        os.makedirs(result_dir, exist_ok=True)
-    st = _abi.RunStats()
-    rc = _lib().pm_run_beta_local_shards(ctypes.byref(desc), pattern_dir.encode(), device, nshards,
-                                         None if lab is None else lab.ctypes.data, result_dir.encode(),
-                                         max_iterations, ctypes.byref(st))
-    if rc != 0:
-        raise _err()
-    return st.as_dict()
+    device (in-process exchange instead of RCCL): parity of the sharded path on one GPU.  Shard 0's statistics."""
+    return run_beta_local_shards_each(graph, pattern_dir, nshards, result_dir, max_iterations, device, labels)[0]
 
 
 def run_beta_local_shards_each(graph, pattern_dir, nshards, result_dir="", max_iterations=0, device=0, labels=None,
                                label_prefix=None, repeats=1):
     """run_beta_local_shards with -v label files (label_prefix, parsed on the device once) or labels, the search
-    repeated `repeats` times (result files from the first) and every shard's statistics (pm_run_beta_local_shards2:
+    repeated `repeats` times (result files from the first) and every shard's statistics (pm_run_beta_local_shards:
     the drop-in executable's mode for a P-partition graph on fewer GPUs than P)."""
     desc = _abi.GraphDesc(graph.n, graph.off.ctypes.data, graph.col.ctypes.data, int(graph.symmetric), graph.nranks,
                           graph.hub_threshold)
@@ -227,10 +216,10 @@ def run_beta_local_shards_each(graph, pattern_dir, nshards, result_dir="", max_i
     if result_dir:
         os.makedirs(result_dir, exist_ok=True)
     st = (_abi.RunStats * nshards)()
-    rc = _lib().pm_run_beta_local_shards2(ctypes.byref(desc), pattern_dir.encode(), device, nshards,
-                                          None if lab is None else lab.ctypes.data,
-                                          None if label_prefix is None else os.fspath(label_prefix).encode(),
-                                          result_dir.encode(), max_iterations, repeats, st)
+    rc = _lib().pm_run_beta_local_shards(ctypes.byref(desc), pattern_dir.encode(), device, nshards,
+                                         None if lab is None else lab.ctypes.data,
+                                         None if label_prefix is None else os.fspath(label_prefix).encode(),
+                                         result_dir.encode(), max_iterations, repeats, st)
     if rc != 0:
         raise _err()
     return [s.as_dict() for s in st]
@@ -271,15 +260,9 @@ def run_rmat_local_shards(scale, p_gen, pattern_dir, nshards, result_dir="", max
                           hub_threshold=DEFAULT_HUB_THRESHOLD):
     """The sharded search over the R-MAT graph with `nshards` shards driven by threads of this process
     on one device: each shard generates its generator ranks' streams on the device and the entries
-    reach their owners in one in-process all-to-all (pm_run_rmat_local_shards)."""
-    if result_dir:
-        os.makedirs(result_dir, exist_ok=True)
-    st = _abi.RunStats()
-    rc = _lib().pm_run_rmat_local_shards(scale, p_gen, pattern_dir.encode(), device, nshards, nranks, hub_threshold,
-                                         result_dir.encode(), max_iterations, ctypes.byref(st))
-    if rc != 0:
-        raise _err()
-    return st.as_dict()
+    reach their owners in one in-process all-to-all (pm_run_rmat_local_shards).  Shard 0's statistics."""
+    return run_rmat_local_shards_each(scale, p_gen, pattern_dir, nshards, result_dir, max_iterations, device, nranks,
+                                      hub_threshold)[0]
 
 
 def run_rmat_local_shards_each(scale, p_gen, pattern_dir, nshards, result_dir="", max_iterations=0, device=0,
@@ -291,9 +274,9 @@ def run_rmat_local_shards_each(scale, p_gen, pattern_dir, nshards, result_dir=""
         os.makedirs(result_dir, exist_ok=True)
     lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.uint64)
     st = (_abi.RunStats * nshards)()
-    rc = _lib().pm_run_rmat_local_shards2(scale, p_gen, pattern_dir.encode(), device, nshards, nranks, hub_threshold,
-                                          None if lab is None else lab.ctypes.data, result_dir.encode(),
-                                          max_iterations, repeats, st)
+    rc = _lib().pm_run_rmat_local_shards(scale, p_gen, pattern_dir.encode(), device, nshards, nranks, hub_threshold,
+                                         None if lab is None else lab.ctypes.data, result_dir.encode(),
+                                         max_iterations, repeats, st)
     if rc != 0:
         raise _err()
     return [s.as_dict() for s in st]

@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI declared in include/pm_abi.h.
+"""ctypes binding of the C-ABI declared in include/pm_abi.h (diagnostics: include/pm_abi_debug.h).
 
 The shared library lib/libpm.so (HIP kernels for gfx950 + host driver) is the
 product; this module only declares signatures.  It fails loudly when the
@@ -125,7 +125,7 @@ class RunStats(ctypes.Structure):
         return {f[0]: getattr(self, f[0]) for f in self._fields_ if f[0] != "reserved"}
 
 
-# (name, restype, argtypes) -- every symbol include/pm_abi.h declares.
+# (name, restype, argtypes) -- every symbol include/pm_abi.h and include/pm_abi_debug.h declare.
 SIGNATURES = [
     ("pm_create", c_vp, [ctypes.POINTER(GraphDesc), c_char_p, ctypes.c_int]),
     ("pm_destroy", None, [c_vp]),
@@ -160,7 +160,7 @@ SIGNATURES = [
     ("pm_create_shard_host_comm", c_vp, [ctypes.POINTER(ShardDesc), c_char_p, ctypes.c_int,
                                          ctypes.POINTER(HostComm)]),
     ("pm_run_beta_local_shards", ctypes.c_int, [ctypes.POINTER(GraphDesc), c_char_p, ctypes.c_int, c_u32, c_vp,
-                                                c_char_p, c_u64, ctypes.POINTER(RunStats)]),
+                                                c_char_p, c_char_p, c_u64, c_u32, ctypes.POINTER(RunStats)]),
     ("pm_rmat_edges", ctypes.c_int, [c_u64, c_u64, c_u64, c_u64, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                      ctypes.POINTER(c_u64)]),
     ("pm_rmat_csr_gpu", ctypes.c_int, [c_u64, c_u64, ctypes.c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
@@ -168,10 +168,8 @@ SIGNATURES = [
     ("pm_create_rmat", c_vp, [c_u64, c_u64, c_char_p, ctypes.c_int, c_u32, c_u64, ctypes.POINTER(ctypes.c_double)]),
     ("pm_create_rmat_shard", c_vp, [c_u64, c_u64, c_char_p, ctypes.c_int, c_u32, c_u64, c_u32, c_u32, c_vp,
                                     ctypes.POINTER(ctypes.c_double)]),
-    ("pm_run_rmat_local_shards", ctypes.c_int, [c_u64, c_u64, c_char_p, ctypes.c_int, c_u32, c_u32, c_u64, c_char_p,
-                                                c_u64, ctypes.POINTER(RunStats)]),
-    ("pm_run_rmat_local_shards2", ctypes.c_int, [c_u64, c_u64, c_char_p, ctypes.c_int, c_u32, c_u32, c_u64, c_vp,
-                                                 c_char_p, c_u64, c_u32, ctypes.POINTER(RunStats)]),
+    ("pm_run_rmat_local_shards", ctypes.c_int, [c_u64, c_u64, c_char_p, ctypes.c_int, c_u32, c_u32, c_u64, c_vp,
+                                                c_char_p, c_u64, c_u32, ctypes.POINTER(RunStats)]),
     ("pm_mt19937_jump_outputs", ctypes.c_int, [c_u32, c_u64, c_vp, c_u64]),
     ("pm_vertex_data_files", ctypes.c_int, [c_vp, c_char_p]),
     ("pm_graph_size", ctypes.c_int, [c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_int)]),
@@ -180,8 +178,6 @@ SIGNATURES = [
                                                ctypes.POINTER(ctypes.c_int)]),
     ("pm_create_edge_list", c_vp, [c_vp, c_u32, ctypes.c_int, c_char_p, ctypes.c_int, c_u32, c_u64,
                                    ctypes.POINTER(ctypes.c_double)]),
-    ("pm_run_beta_local_shards2", ctypes.c_int, [ctypes.POINTER(GraphDesc), c_char_p, ctypes.c_int, c_u32, c_vp,
-                                                 c_char_p, c_char_p, c_u64, c_u32, ctypes.POINTER(RunStats)]),
     ("pm_graph_partitions", ctypes.c_int, [c_char_p]),
     ("pm_read_graph_shard", ctypes.c_int, [c_char_p, c_u32, c_u32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                            ctypes.POINTER(c_vp), ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_int),

@@ -1,5 +1,5 @@
 // Internal declarations shared by the HIP kernels (pm_kernels.hip) and the
-// host driver / C-ABI (pm_api.hip).
+// host side (pm_host.hpp: context, driver, C-ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -658,7 +658,7 @@ uint32_t launch_post_tp(Ctx& c, const NlcLine& line);
 
 LineArgs make_line_args(const Ctx& c, const NlcLine& line);
 
-uint64_t* pinned(Ctx& c, size_t words);  // pinned host staging (pm_api.hip)
+uint64_t* pinned(Ctx& c, size_t words);  // pinned host staging (pm_driver.hip)
 // PM_DEBUG_SYNC=1 (diagnostics): the stream is synchronised at each named point and a device fault is reported
 // with the point's name and the shard (=2: every point passed is also printed); no-op otherwise.
 void debug_point(Ctx& c, const char* where);

@@ -18,7 +18,7 @@
 //   * one process, a P-partition graph (P > 1) and at least P GPUs: P shards,
 //     one thread and one GPU each, one RCCL communicator (xGMI);
 //   * one process, P > 1 and fewer GPUs than P: the P shards in-process on
-//     device 0 (pm_run_beta_local_shards2);
+//     device 0 (pm_run_beta_local_shards);
 //   * P = 1, or a directed graph (the sharded search takes symmetric graphs): one context holds the whole graph
 //     (launched: on rank 0).
 // PM_SHARDS=<k> overrides the shard count of a one-process run (any k: the
@@ -197,9 +197,9 @@ int run_local_shards(const Options& o, uint32_t nshards) {
   pm_graph_desc d{n, off, col, symmetric, nranks, hub};
   std::vector<pm_run_stats> st(nshards);
   const char* dev = std::getenv("PM_DEVICE");
-  const int rc = pm_run_beta_local_shards2(&d, o.pattern_dir.c_str(), dev ? std::atoi(dev) : 0, nshards, nullptr,
-                                           o.vertex_metadata.empty() ? nullptr : o.vertex_metadata.c_str(),
-                                           o.result_dir.c_str(), o.max_iterations, 1, st.data());
+  const int rc = pm_run_beta_local_shards(&d, o.pattern_dir.c_str(), dev ? std::atoi(dev) : 0, nshards, nullptr,
+                                          o.vertex_metadata.empty() ? nullptr : o.vertex_metadata.c_str(),
+                                          o.result_dir.c_str(), o.max_iterations, 1, st.data());
   pm_free_host(off);
   pm_free_host(col);
   if (rc != 0) {

@@ -48,7 +48,7 @@
  *   pm_create_shard_host_comm     pm_create_shard with the exchanges through caller-supplied host
  *                                 collectives (pm_host_comm): the reference's own MPI transport
  *                                 (new_mailbox.hpp:358-405, impl/vertex_data.hpp:114-126) or a gloo group
- *   pm_run_rmat_local_shards2     the N-rank delegate partition of generate_rmat's graph
+ *   pm_run_rmat_local_shards      the N-rank delegate partition of generate_rmat's graph
  *                                 (delegate_partitioned_graph.ipp:1402-1648, 346-355) run as N shards on
  *                                 one device, with every shard's statistics (balance / N-GPU projection)
  *
@@ -227,10 +227,14 @@ pm_ctx* pm_create_shard_host_comm(const pm_shard_desc* shard, const char* patter
 
 /* nshards shards of one search run by threads of this process on one device (the
  * partitioning of pm_create_shard with an in-process exchange): parity of the sharded
- * path on a single GPU.  labels may be NULL (degree labels). */
+ * path on a single GPU, and the drop-in executable's mode for a P-partition graph on fewer GPUs than P
+ * (run_pattern_matching_beta).  Labels: -v label files label_prefix, parsed on the device once and shared by
+ * the shards (vertex_data_db.hpp:137-257); with a NULL prefix `labels`; degree labels when both are NULL.
+ * The search runs `repeats` times (>= 1; result files from the first run, statistics from the last);
+ * per_shard[q] for q < nshards receives every shard's statistics (may be NULL). */
 int pm_run_beta_local_shards(const pm_graph_desc* graph, const char* pattern_dir, int device, uint32_t nshards,
-                             const uint64_t* labels, const char* result_dir, uint64_t max_iterations,
-                             pm_run_stats* out);
+                             const uint64_t* labels, const char* label_prefix, const char* result_dir,
+                             uint64_t max_iterations, uint32_t repeats, pm_run_stats* per_shard);
 
 /* One shard of a sharded search over the R-MAT graph of generate_rmat, built on the device
  * (collective over the nshards processes): shard q generates the edge streams of generator ranks
@@ -243,24 +247,13 @@ pm_ctx* pm_create_rmat_shard(uint64_t scale, uint64_t p_gen, const char* pattern
                              uint64_t hub_threshold, uint32_t nshards, uint32_t shard, const uint8_t* unique_id,
                              double* gen_seconds);
 /* The same with nshards shards driven by threads of this process on one device (in-process exchange):
- * the whole sharded path -- generation, all-to-all, delegates, replica -- on a one-GPU box. */
+ * the whole sharded path -- generation, all-to-all, delegates, replica -- on a one-GPU box.  labels may be
+ * NULL (degree labels); the search runs `repeats` times (>= 1; result files from the first run, statistics
+ * from the last); per_shard[q] for q < nshards receives every shard's statistics (may be NULL): the partition
+ * balance and per-shard device times of the N-GPU layout, measured with the shards on one device. */
 int pm_run_rmat_local_shards(uint64_t scale, uint64_t p_gen, const char* pattern_dir, int device, uint32_t nshards,
-                             uint32_t nranks, uint64_t hub_threshold, const char* result_dir, uint64_t max_iterations,
-                             pm_run_stats* out);
-/* The same with labels (NULL: degree labels), the search run `repeats` times (>= 1; result files from the
- * first run, statistics from the last) and every shard's statistics: per_shard[q] for q < nshards (the
- * partition balance and per-shard device times of the N-GPU layout, measured with the shards on one device). */
-int pm_run_rmat_local_shards2(uint64_t scale, uint64_t p_gen, const char* pattern_dir, int device, uint32_t nshards,
-                              uint32_t nranks, uint64_t hub_threshold, const uint64_t* labels, const char* result_dir,
-                              uint64_t max_iterations, uint32_t repeats, pm_run_stats* per_shard);
-
-/* The same with every shard's statistics (per_shard[q], q < nshards; may be NULL), the search run `repeats`
- * times (result files from the first run) and -v label files: label_prefix (NULL: `labels`, or degree labels
- * when both are NULL) is parsed on the device once and shared by the shards (vertex_data_db.hpp:137-257).
- * The drop-in executable's mode for a P-partition graph on fewer GPUs than P (run_pattern_matching_beta). */
-int pm_run_beta_local_shards2(const pm_graph_desc* graph, const char* pattern_dir, int device, uint32_t nshards,
-                              const uint64_t* labels, const char* label_prefix, const char* result_dir,
-                              uint64_t max_iterations, uint32_t repeats, pm_run_stats* per_shard);
+                             uint32_t nranks, uint64_t hub_threshold, const uint64_t* labels, const char* result_dir,
+                             uint64_t max_iterations, uint32_t repeats, pm_run_stats* per_shard);
 
 /* Graph files of a sharded run.  pm_graph_partitions: P of <base>_<r>_of_<P> (-1: none found).
  * pm_read_graph_shard: shard `shard` of `nshards` read straight from the files, as pm_create_shard takes it --
@@ -325,29 +318,7 @@ int pm_write_label_text(const uint64_t* labels, uint64_t n, const char* prefix, 
 /* Parsed pattern directory as JSON text (host only; loader check). */
 int pm_pattern_summary(const char* pattern_dir, char* buf, uint64_t buflen);
 
-/* Diagnostics: average time of `reps` launches of superstep-0 kernel variant
- * (0 = product kernel; others are ablation builds used by tools/ubench.py). */
-int pm_debug_time_lcc_first(pm_ctx* ctx, int variant, int reps, float* ms_out);
-/* Diagnostics: a one-rank RCCL collective of `bytes` (op 0 ncclAllGather, 1 ncclAllReduce u64 sum),
-   result checked: 0 = right, 1 = wrong, -1 = error (pm_last_error). */
-int pm_debug_rccl_selftest(int device, uint64_t bytes, int op);
-/* Diagnostics: HBM copy bandwidth of a 16-B nontemporal copy kernel over two `bytes` buffers (read + write
-   bytes per second / 1e9), the measured ceiling beside the datasheet peak. */
-int pm_debug_copy_gbs(int device, uint64_t bytes, int reps, double* gbs);
-/* Diagnostics: the floor of the first later superstep's neighbour-T_pub gathers: superstep 0
-   runs, its light survivors' alive M entries are collected as code indices in record order, and gather-only
-   kernels are timed over them (variant 0 record order, 1 index stream only, 2 XCD-sliced buckets, 3 the buckets
-   spread over every XCD, 4 uniformly random, 5 sorted, 6 distinct-line misses of a 4 GiB buffer (FETCH_SIZE calibration),
-   7 the bucketing pass).  info[0] entries, [1] checksum of the gathered codes, [2] code array bytes. */
-int pm_debug_gather_floor(pm_ctx* ctx, int variant, int reps, float* ms_out, uint64_t* info);
-/* Diagnostics: superstep-0 tiling statistics (real entries, loaded slots, rows, tiles, ranges, heavy rows). */
-int pm_debug_layout_stats(pm_ctx* ctx, uint64_t* out, uint64_t n);
-
-/* Diagnostics: T_pub census (both ping-pong buffers) -- out[0], out[1]: nonzero entries of buffer 0 / 1,
-   out[2]: positions with a nonzero entry in either buffer that are not in the current slist (the invariant
-   the search-start clear relies on: 0).  deferred_reset != 0 first runs the search start's reset as a search
-   does (deferred, then flushed in one launch), so out[0..2] must all be 0 afterwards. */
-int pm_debug_tpub_census(pm_ctx* ctx, int deferred_reset, uint64_t* out);
+/* (The diagnostic entry points of the library are declared in pm_abi_debug.h.) */
 
 /* Build info: returns the offload arch the kernels were compiled for ("gfx950"). */
 const char* pm_build_arch(void);

@@ -16,9 +16,16 @@ GOLDEN = os.path.join(pmtest.ROOT, "tests", "golden")
 
 def test_library_exports_every_declared_symbol():
     lib = _abi.load()
-    header = open(os.path.join(pmtest.ROOT, "include", "pm_abi.h")).read()
-    declared = set(re.findall(r"\b(pm_[a-z_0-9]+)\s*\(", header))
-    assert len(declared) >= 15
+    declared = set()
+    for name in ("pm_abi.h", "pm_abi_debug.h"):
+        header = open(os.path.join(pmtest.ROOT, "include", name)).read()
+        found = set(re.findall(r"\b(pm_[a-z_0-9]+)\s*\(", header))
+        if name == "pm_abi.h":  # the header an integrator binds against carries no diagnostics
+            assert len(found) >= 15
+            assert not [s for s in found if s.startswith("pm_debug_")]
+            assert "pm_debug_" not in header and "pm_abi_debug.h\"" not in header
+        declared |= found
+    assert any(s.startswith("pm_debug_") for s in declared)
     bound = {name for name, _, _ in _abi.SIGNATURES}
     assert declared == bound, declared ^ bound
     for name in declared:
@@ -33,6 +40,20 @@ def test_create_without_gpu_fails_loudly(tree_pattern):
     g = pm.Graph.from_edges([0, 1], [1, 0], n=2)
     with pytest.raises(pm.PMError, match="no HIP device|not gfx950"):
         pm.PatternMatcher(g, tree_pattern)
+
+
+@pytest.mark.parametrize("nshards", [0, 65])
+def test_local_shards_refuse_bad_shard_count(tree_pattern, nshards):
+    """Checked before the device is touched; the message thrown inside the entry point's wrapper reaches
+    pm_last_error on the calling thread."""
+    g = pm.Graph.from_edges([0, 1], [1, 0], n=2)
+    with pytest.raises(pm.PMError, match="pm_run_beta_local_shards: 1..64 shards"):
+        pm.run_beta_local_shards(g, tree_pattern, nshards)
+
+
+def test_rmat_local_shards_refuse_bad_shard_count(tree_pattern):
+    with pytest.raises(pm.PMError, match="pm_run_rmat_local_shards: 1..64 shards"):
+        pm.run_rmat_local_shards(8, 2, tree_pattern, 0)
 
 
 def test_pattern_loader_tree(tree_pattern):

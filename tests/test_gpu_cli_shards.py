@@ -67,7 +67,7 @@ def test_cli_partitioned_graph_in_process(tmp_path, pattern, hub):
 
 def test_cli_ingested_four_partitions_label_files(tmp_path):
     """ingest_edge_list -u 1 -n 4 of a text edge list, -v label files (hash labels, 64 letters), 4-cycle pattern:
-    the CLI runs 4 in-process shards with the labels parsed on the device (pm_run_beta_local_shards2)."""
+    the CLI runs 4 in-process shards with the labels parsed on the device (pm_run_beta_local_shards)."""
     scale, p_gen, nranks = 16, 4, 4
     und = [oracle.rmat_rank_edges(scale, p_gen, r) for r in range(p_gen)]
     u = np.concatenate([x[0] for x in und])

@@ -123,7 +123,7 @@ def test_c5_s27_ingested_label_files(tmp_path, monkeypatch):
     made by make_rmat_fixture.py -- ingest == generate is checked bit for bit at S=18 above); the result does not
     depend on the TDS chunk cap; and C5 as BASELINE runs it, an 8-way partition: the ingested CSR as 8 in-process
     shards (delegates split by target owner, NLC lines split by owner) with the -v files parsed once on the device
-    (pm_run_beta_local_shards2, the drop-in executable's path for 8 partitions on one GPU) gives the same result.
+    (pm_run_beta_local_shards, the drop-in executable's path for 8 partitions on one GPU) gives the same result.
     (An alphabet of 8 or 64 letters makes the 4-cycle enumeration ~10^13 edges at S=27 -- it grows ~6x per
     scale from the oracle's S=20-22 counts -- for the reference as for this path; 256 letters keep it
     tractable: tools/c5_at_size.py, DESIGN.md.)"""

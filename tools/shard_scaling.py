@@ -1,6 +1,6 @@
 """One search sharded over N in-process shards (one GPU), N = 1, 2, 4, 8: every shard's statistics.
 
-pm_run_rmat_local_shards2 generates the R-MAT graph shard by shard on the device (each shard its generator
+pm_run_rmat_local_shards generates the R-MAT graph shard by shard on the device (each shard its generator
 ranks' streams, the entries routed to their owners), sets the labels, and runs the search `repeats` times;
 the shards take turns on the chip (ThreadComm), so each shard's device times are its own work, with no
 contention from the others.  Per N the tool records, for every shard: the superstep-0 kernel time, the
