@@ -398,6 +398,18 @@ class PatternMatcher:
         return {"nshards": ns.value, "shard": sh.value, "comm_ranks": cr.value,
                 "transport": _abi.TRANSPORTS.get(tr.value, str(tr.value))}
 
+    LAYOUT_STATS = ("entries", "slots", "rows", "tiles", "ranges", "heavy_rows", "layout_us", "max_nrel", "max_nadm",
+                    "max_nkeep", "k1_wide", "phase_a_mask", "long_row_supersteps")
+
+    def layout_stats(self):
+        """Superstep-0 tiling of the current labels and the specialisations it selects (pm_debug_layout_stats):
+        max_nrel > 4 = k1_wide (the wide k_lcc_first instantiation), max_nkeep > 4 = the LDS keep_bits loop,
+        phase_a_mask bits 0..3 = light ranges with nadm <= 1, 2, 3..4, and the full label test;
+        long_row_supersteps = pull supersteps of the last search's first LCC call that worked rows in pieces."""
+        out = np.zeros(len(self.LAYOUT_STATS), np.uint64)
+        self._check(_lib().pm_debug_layout_stats(self._ctx, out.ctypes.data, out.shape[0]))
+        return {k: int(v) for k, v in zip(self.LAYOUT_STATS, out)}
+
     def tpub_census(self, deferred_reset=False):
         """(nonzero T_pub entries of buffer 0, of buffer 1, positions nonzero in either buffer outside the
         current slist) -- diagnostics of the invariant the search-start clear relies on

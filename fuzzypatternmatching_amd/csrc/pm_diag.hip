@@ -149,10 +149,19 @@ int pm_debug_time_lcc_first(pm_ctx* ctx, int variant, int reps, float* ms_out) {
 // entries of the scanned runs, [1] slots loaded (padding included), [2]
 // scanned rows, [3] tiles, [4] ranges, [5] heavy rows, [6] microseconds of
 // the last label-major layout + tiling build (one-time, outside any search).
+// Which superstep-0 specialisations the tiling selects, over its ranges with
+// rows (host table only): [7] max nrel, [8] max nadm, [9] max nkeep,
+// [10] k1_wide (the k_lcc_first<0, true> instantiation runs), [11] mask of
+// the phase-A cases its light ranges take in k1_light_tile (bit 0: nadm <= 1,
+// 1: nadm == 2, 2: nadm 3..4, 3: the full label test -- nadm > 4, and every
+// range of a k1_wide tiling).  [12] pull supersteps of the last search's first
+// LCC call that put rows on the long-row list (worked in pieces by
+// k_lcc_step_pieces); 0 before the first search.
 int pm_debug_layout_stats(pm_ctx* ctx, uint64_t* out, uint64_t n) {
   return pm::ctx_call(ctx, [&] {
-    uint64_t st[7] = {0, 0, 0, ctx->ntiles, ctx->ktab.empty() ? 0 : ctx->ktab.size() - 1, ctx->nheavy,
-                      static_cast<uint64_t>(ctx->layout_seconds * 1e6)};
+    uint64_t st[13] = {0, 0, 0, ctx->ntiles, ctx->ktab.empty() ? 0 : ctx->ktab.size() - 1, ctx->nheavy,
+                       static_cast<uint64_t>(ctx->layout_seconds * 1e6), 0, 0, 0, ctx->k1_wide ? 1u : 0u, 0, 0};
+    for (size_t ss = 1; ss < ctx->long_seen.size(); ++ss) st[12] += ctx->long_seen[ss] ? 1 : 0;
     std::vector<uint64_t> offp(ctx->n + 1), offr(ctx->n + 1);
     PM_HIP_CHECK(hipMemcpy(offp.data(), ctx->d_offp, offp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     PM_HIP_CHECK(hipMemcpy(offr.data(), ctx->d_offr, offr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -161,8 +170,14 @@ int pm_debug_layout_stats(pm_ctx* ctx, uint64_t* out, uint64_t n) {
       st[0] += offr[R.end] - offr[R.start];
       st[1] += offp[R.end] - offp[R.start];
       st[2] += R.end - R.start;
+      if (R.end <= R.start) continue;
+      st[7] = std::max<uint64_t>(st[7], R.nrel);
+      st[8] = std::max<uint64_t>(st[8], R.nadm);
+      st[9] = std::max<uint64_t>(st[9], R.nkeep);
+      if (R.kind < static_cast<uint32_t>(pm::kHeavyKind))
+        st[11] |= (ctx->k1_wide || R.nadm > 4) ? 8u : R.nadm <= 1 ? 1u : R.nadm == 2 ? 2u : 4u;
     }
-    for (uint64_t i = 0; i < n && i < 7; ++i) out[i] = st[i];
+    for (uint64_t i = 0; i < n && i < 13; ++i) out[i] = st[i];
   });
 }
 

@@ -27,7 +27,13 @@ int pm_debug_copy_gbs(int device, uint64_t bytes, int reps, double* gbs);
    spread over every XCD, 4 uniformly random, 5 sorted, 6 distinct-line misses of a 4 GiB buffer (FETCH_SIZE calibration),
    7 the bucketing pass).  info[0] entries, [1] checksum of the gathered codes, [2] code array bytes. */
 int pm_debug_gather_floor(pm_ctx* ctx, int variant, int reps, float* ms_out, uint64_t* info);
-/* Diagnostics: superstep-0 tiling statistics (real entries, loaded slots, rows, tiles, ranges, heavy rows). */
+/* Diagnostics: superstep-0 tiling statistics, the first n of: [0] real entries, [1] loaded slots, [2] rows,
+   [3] tiles, [4] ranges, [5] heavy rows, [6] microseconds of the last layout + tiling build; then which
+   specialisations the tiling selects, over its ranges with rows: [7] max nrel (relevant label runs),
+   [8] max nadm (merged runs), [9] max nkeep (template vertices of one label), [10] k1_wide (some nrel > 4:
+   k_lcc_first<0, true> runs), [11] mask of the phase-A cases the light ranges take (bit 0 nadm <= 1, 1 nadm == 2,
+   2 nadm 3..4, 3 the full label test: nadm > 4, and every range when k1_wide); [12] pull supersteps of the last
+   search's first LCC call that listed long rows for k_lcc_step_pieces (0 before the first search). */
 int pm_debug_layout_stats(pm_ctx* ctx, uint64_t* out, uint64_t n);
 
 /* Diagnostics: T_pub census (both ping-pong buffers) -- out[0], out[1]: nonzero entries of buffer 0 / 1,
