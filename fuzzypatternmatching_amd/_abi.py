@@ -119,6 +119,9 @@ class RunStats(ctypes.Structure):
         ("replica_entries", c_u64),
         ("comm_seconds", ctypes.c_double),
         ("path_batches", c_u64),
+        ("shard_in_entries", c_u64),
+        ("shard_push_supersteps", c_u64),
+        ("shard_push_messages", c_u64),
     ]
 
     def as_dict(self):

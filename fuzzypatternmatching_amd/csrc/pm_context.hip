@@ -113,12 +113,30 @@ pm_ctx* create_ctx(const CtxInput& in, const char* pattern_dir, int device) {
   std::vector<uint32_t> tin_col;
   const uint64_t* soff = in.off;
   const uint32_t* scol = in.col;
+  bool scol_on_device = in.col_on_device;
+  uint64_t snnz = c->nnz;
   size_t arena = 0;
   bool any_sv = false;
   std::string build_err;
+  // a shard of a directed graph holds out-rows: the in-rows of the vertices it owns come from every shard's
+  // (collective; a shard that fails in it reports through build_err and still takes part in the agreement below)
+  struct InCol {
+    uint32_t* p = nullptr;
+    void now() {
+      if (p) (void)hipFree(p);
+      p = nullptr;
+    }
+    ~InCol() { now(); }
+  } in_col;
+  if (!c->symmetric && in.nshards > 1) build_shard_in_rows(*c, in, build_err, tin_off, &in_col.p);
   try {
-    if (!c->symmetric) {
-      if (in.nshards > 1) throw std::runtime_error("directed input graphs are supported on one shard only");
+    if (!build_err.empty()) throw std::runtime_error(build_err);
+    if (!c->symmetric && in.nshards > 1) {
+      soff = tin_off.data();
+      scol = in_col.p;
+      scol_on_device = true;
+      snnz = tin_off[c->n];
+    } else if (!c->symmetric) {
       if (in.in_off && in.in_col) {
         soff = in.in_off;
         scol = in.in_col;
@@ -169,7 +187,14 @@ pm_ctx* create_ctx(const CtxInput& in, const char* pattern_dir, int device) {
       c->held_rows += ld != 0;
       if (ld && d >= c->hub_threshold && c->nshards > 1) c->held_hub_entries += ld;
     }
-    c->split_hubs = c->nshards > 1 && !c->hubs_host.empty();
+    // (a directed graph's in-rows are whole on their owners, delegates' too: nothing to combine)
+    c->split_hubs = c->nshards > 1 && c->symmetric && !c->hubs_host.empty();
+    // a shard context of a directed graph (one shard with a communicator included): the rows held here, which
+    // the layout copies and pads, are the in-rows -- not the out-rows the shard was given
+    if (!c->symmetric && (c->nshards > 1 || !c->ldeg_host.empty())) {
+      c->ldeg_host.resize(c->n);
+      for (uint64_t v = 0; v < c->n; ++v) c->ldeg_host[v] = static_cast<uint32_t>(soff[v + 1] - soff[v]);
+    }
     for (uint64_t j = c->shard; c->split_hubs && j < c->hubs_host.size(); j += c->nshards)
       c->hub_area += c->deg_host[c->hubs_host[j]];
     // device graph + state; padded slot count of the rows scanned here (label independent)
@@ -256,15 +281,16 @@ pm_ctx* create_ctx(const CtxInput& in, const char* pattern_dir, int device) {
   if (const char* e = std::getenv("PM_FORCE_PULL")) c->force_pull = std::string(e) == "1" && c->symmetric;
   // default labels = degree labels; the id-major adjacency is staged in the
   // M column buffer and permuted into the label-major d_colp
-  if (c->nnz) {
-    if (in.col_on_device) {
-      PM_HIP_CHECK(hipMemcpy(c->d_mcol, scol, c->nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+  if (snnz) {
+    if (scol_on_device) {
+      PM_HIP_CHECK(hipMemcpy(c->d_mcol, scol, snnz * sizeof(uint32_t), hipMemcpyDeviceToDevice));
       col_release.now();
+      in_col.now();
     } else {
       // pinned staging: the caller's pages are registered for the copy, so the
       // adjacency moves by DMA without a bounce through driver staging buffers
-      PinnedRange pin(scol, c->nnz * sizeof(uint32_t));
-      PM_HIP_CHECK(hipMemcpy(c->d_mcol, scol, c->nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+      PinnedRange pin(scol, snnz * sizeof(uint32_t));
+      PM_HIP_CHECK(hipMemcpy(c->d_mcol, scol, snnz * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
   }
   set_degree_labels(*c);
@@ -298,7 +324,7 @@ void destroy_ctx(pm_ctx* c) {
                   c->d_tcode, c->d_rarea, c->d_rbase, c->d_rcnt, c->d_rofs, c->d_hrec, c->d_srec, c->d_rscan_tmp, c->d_cdesc,
                   c->d_xsend, c->d_xrecv, c->d_xent_send,
                   c->d_xent_recv, c->d_xcnt, c->d_rmoff, c->d_rmcol, c->d_xred, c->d_hubinfo, c->d_moff, c->d_hubpart, c->d_xsplit, c->d_push,
-                  c->d_lrows, c->d_lscr, c->d_clstat, c->d_lsrc, c->d_ldels,
+                  c->d_lrows, c->d_lscr, c->d_clstat, c->d_lsrc, c->d_ldels, c->d_pushx,
                   };
   for (void* p : ptrs)
     if (p) (void)hipFree(p);

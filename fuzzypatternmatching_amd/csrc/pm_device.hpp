@@ -183,6 +183,81 @@ __device__ __forceinline__ void block_atomic_add(unsigned long long* dst, uint64
 }
 
 
+// ---------------------------------------------------------------------------
+// Push form of a later LCC superstep: what its kernels (pm_kernels.hip) and the sharded senders and receivers
+// (pm_push_shard.hip) share.
+__device__ __forceinline__ int64_t m_find(const uint32_t* __restrict__ mcol, uint64_t b, uint32_t len,
+                                          const uint32_t* __restrict__ perm, uint32_t vid) {
+  uint64_t lo = b, hi = b + len;
+  while (lo < hi) {  // first entry whose neighbour id >= vid
+    const uint64_t mid = (lo + hi) >> 1;
+    if (perm[mcol[mid] & kPosMask] < vid) lo = mid + 1; else hi = mid;
+  }
+  return lo < b + len ? static_cast<int64_t>(lo) : -1;
+}
+
+// Entry-parallel: each wave takes 64 slist entries (rows); rows of at most kPushLong entries are walked
+// flattened over the wave (every lane takes every 64th entry of their concatenation, four in flight), longer
+// rows (R-MAT hubs: a lane walking a row of 10^5..10^6 entries, each with a binary search, took seconds) are
+// cut into kPushLong-entry pieces appended to a list that every wave of a second launch works through.
+static constexpr uint32_t kPushLong = 256;
+
+struct PushArgs {
+  const uint64_t* offp;
+  const uint32_t* slist;
+  const uint32_t* nS;
+  const uint16_t* tcur;
+  uint16_t* tnxt;
+  uint16_t* tst;
+  const uint32_t* perm;
+  uint32_t* mcol;
+  const uint32_t* mlen;
+  uint32_t* malive;
+  uint32_t* tn;
+  unsigned long long* pieces;   // (slist index << 32 | piece) of the long rows
+  unsigned long long* npieces;  // zeroed before the launches (the send and the verify have lists of their own)
+  uint64_t piece_cap;
+};
+
+// Receiver half: u takes T_pub(v) = Tv from v (id vid).
+__device__ __forceinline__ void push_receive(const PushArgs& a, const uint16_t* s_adj, uint32_t u, uint32_t v,
+                                             uint32_t vid, uint16_t Tv) {
+  const uint16_t Tu = a.tcur[u];
+  if (!Tu || !(Tv & nbr_mask(Tu, s_adj))) return;  // u not in S, or not a valid parent
+  // (bits already present are not sent again: a hub's TN word takes one atomic per new bit instead of one per
+  // neighbour, which serialised on the word)
+  if ((a.tn[u] & Tv) != Tv) atomicOr(&a.tn[u], static_cast<uint32_t>(Tv));
+  const int64_t e = m_find(a.mcol, a.offp[u], a.mlen[u], a.perm, vid);
+  if (e >= 0) {
+    const uint32_t x = a.mcol[e];
+    if ((x & kPosMask) == v && (x & kAlive)) atomicOr(&a.mcol[e], kFlag);
+  }
+}
+
+// Sender entry: v (id vid, T_pub Tv) delivers to the neighbour in entry m.
+__device__ __forceinline__ void push_send_entry(const PushArgs& a, const uint16_t* s_adj, uint32_t v, uint32_t vid,
+                                                uint16_t Tv, uint32_t m) {
+  if (!(m & kAlive)) return;
+  push_receive(a, s_adj, m & kPosMask, v, vid, Tv);
+}
+
+// Appends the pieces of a long row (slist index i, len entries); false when the list is full.
+__device__ __forceinline__ bool push_pieces(const PushArgs& a, uint64_t i, uint32_t len) {
+  const uint32_t np = (len + kPushLong - 1) / kPushLong;
+  const unsigned long long b = atomicAdd(a.npieces, static_cast<unsigned long long>(np));
+  if (b + np > a.piece_cap) {  // full: the reserved slots below the cap are marked empty
+    for (uint64_t q = b; q < a.piece_cap && q < b + np; ++q) a.pieces[q] = ~0ull;
+    return false;
+  }
+  for (uint32_t q = 0; q < np; ++q) a.pieces[b + q] = (static_cast<unsigned long long>(i) << 32) | q;
+  return true;
+}
+
+// The launch arguments of a push superstep (pm_kernels.hip): the send's (a) and the verify's (av), their piece
+// lists zeroed; and the verify launches alone, which end the superstep (T_pub buffers swapped).
+void push_prepare(Ctx& c, PushArgs& a, PushArgs& av);
+void launch_push_verify(Ctx& c, const PushArgs& av, uint64_t* d_slot);
+
 __device__ __forceinline__ bool pos_ok(uint16_t T, int k, const LineArgs& la) {
   return la.lok[k] && ((T >> la.I[k]) & 1u);
 }

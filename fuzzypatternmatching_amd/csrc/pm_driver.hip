@@ -135,8 +135,11 @@ LccOut lcc_call(Ctx& c, bool init_step) {
     c.events.push_back(e);
   }
   std::vector<hipEvent_t>& ev = c.events;  // [0..D] superstep bounds, [D+1], [D+2] superstep-0 kernel
-  // (a dense superstep-0 state is never packed: with D >= 2 the hand-off follows a later superstep)
-  const uint64_t handoff_ss = D == 1 ? 0 : std::max<uint64_t>(1, std::min<uint64_t>(c.handoff_ss, D - 1));
+  // (a dense superstep-0 state is never packed: with D >= 2 the hand-off follows a later superstep; a directed
+  // graph's state is never dense, so PM_HANDOFF=0 replicates it straight after superstep 0)
+  const uint64_t handoff_ss =
+      D == 1 ? 0 : std::max<uint64_t>(c.symmetric ? 1 : 0, std::min<uint64_t>(c.handoff_ss, D - 1));
+  if (init_step) c.push_msgs.clear();
   zero_later(c, c.d_counts, D * W * sizeof(uint64_t));  // kernels add into the slots
   // the search's reset fills go with superstep 0's own (one launch, before the call's timing event)
   if (init_step) queue_lcc_first_fills(c);
@@ -176,8 +179,10 @@ LccOut lcc_call(Ctx& c, bool init_step) {
       // for the next superstep's pulls; a one-superstep pattern goes to the replica at once
       if (c.split_hubs) shard_hub_combine(c, slot);
       debug_point(c, "delegate combine"); debug_watch(c, "delegate combine");
-      if (handoff_ss > 0) shard_codes_after_first(c);
-      else {
+      // (the codes serve the pull form; a directed graph's push-form supersteps carry T_pub in their messages)
+      if (handoff_ss > 0) {
+        if (c.symmetric) shard_codes_after_first(c);
+      } else {
         shard_replicate(c);
         handoff();
       }
@@ -186,8 +191,12 @@ LccOut lcc_call(Ctx& c, bool init_step) {
       if (!c.lcc_started) throw std::runtime_error("LCC without an initial step: state map is empty");
       // pull form while M is known symmetric (the first call on a symmetric
       // graph: no cycle flag set yet); push form otherwise
-      if (!c.force_pull && (!c.symmetric || !init_step)) launch_lcc_push(c, slot);
-      else {
+      if (!c.force_pull && (!c.symmetric || !init_step)) {
+        // a sharded directed search before the replica: the receivers of other shards get messages
+        if (c.comm && !c.replicated) launch_lcc_push_sharded(c, slot);
+        else launch_lcc_push(c, slot);
+        debug_point(c, "push superstep"); debug_watch(c, "push superstep");
+      } else {
         // S collapses in the first later supersteps (S=28 tree: 9.8 M -> 0.8 M -> 26 k): the next
         // supersteps, the NLC lines and the next reset walk the live entries only.  (Appending the live
         // entries inside the superstep, one counter reservation per 64-entry chunk, measured 1.2 ms slower
@@ -206,7 +215,7 @@ LccOut lcc_call(Ctx& c, bool init_step) {
       if (init_step && ss == handoff_ss) {
         shard_replicate(c);
         handoff();
-      } else if (init_step && ss < handoff_ss) {
+      } else if (init_step && ss < handoff_ss && c.symmetric) {
         shard_tpub_exchange(c);
       }
       debug_point(c, "superstep end"); debug_watch(c, "superstep end");
@@ -733,6 +742,9 @@ void run_beta(Ctx& c, const std::string& out_dir, uint64_t max_iterations, pm_ru
   s.shard_ss0_entries = first_scanned;
   s.shard_ss0_survivors = first_surv;
   s.shard_sharded_ms = c.comm ? c.sharded_ms : 0.0;
+  s.shard_in_entries = c.in_entries;
+  s.shard_push_supersteps = c.push_msgs.size();
+  for (uint64_t m : c.push_msgs) s.shard_push_messages += m;
   if (c.comm) {
     s.comm_calls = c.comm->calls - comm_calls0;
     s.comm_bytes = c.comm->bytes - comm_bytes0;

@@ -80,6 +80,11 @@ void set_degree_labels(Ctx& c);
 pm_ctx* create_ctx(const CtxInput& in, const char* pattern_dir, int device);
 pm_ctx* create_ctx(const pm_graph_desc* g, const char* pattern_dir, int device);
 void destroy_ctx(pm_ctx* c);
+// pm_push_shard.hip: the in-rows of the vertices this shard of a directed graph owns, from every shard's
+// out-rows (collective; see there).  Fills in_off (n + 1, host), *d_in_col (device, the caller frees it) and
+// c.rdeg_host (every vertex's in-degree); a failure on any shard leaves a message in err on every shard.
+void build_shard_in_rows(Ctx& c, const CtxInput& in, std::string& err, std::vector<uint64_t>& in_off,
+                         uint32_t** d_in_col);
 void relayout(Ctx& c);
 
 // --- pm_driver.hip: what a search executes -----------------------------------------------------------------------

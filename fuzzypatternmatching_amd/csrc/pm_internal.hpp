@@ -336,6 +336,9 @@ struct Ctx {
   // T_state, M rows) is all-gathered into a replica held by every shard
   // (shard_replicate): the rest of the search -- later supersteps, NLC lines,
   // later LCC calls -- runs on the replica exactly as on one GPU.
+  // A directed graph: the rows held are the in-rows of the owned ids, built from every
+  // shard's out-rows at construction; no code or T_pub exchange -- the push-form supersteps before the replica
+  // send T_pub with their messages (launch_lcc_push_sharded).
   uint32_t nshards = 1, shard = 0;
   uint64_t held_rows = 0;         // nonempty rows this context holds (a shard: owned rows + delegate shares)
   uint64_t held_hub_entries = 0;  // entries of the delegate shares it holds
@@ -372,6 +375,11 @@ struct Ctx {
   uint64_t xcode_max = 0;
   uint64_t* d_xred = nullptr;     // host-vector all-reduce staging
   size_t xred_cap = 0;
+  // sharded directed graph (pm_push_shard.hip): entries of the in-rows built here at construction; the
+  // sharded push supersteps' counters and cursors; messages this shard sent in each of the last search's
+  uint64_t in_entries = 0;
+  void* d_pushx = nullptr;
+  std::vector<uint64_t> push_msgs;
 
   // host side of the driver loop
   uint64_t* h_pin = nullptr;      // pinned staging for counter read-backs
@@ -595,6 +603,9 @@ void ensure_slist2(Ctx& c);
 // Push form of a later superstep (send + verify launches): directed inputs and
 // LCC calls after the first (M may be asymmetric there).
 void launch_lcc_push(Ctx& c, uint64_t* d_slot);
+// The same before the replica of a sharded directed search (pm_push_shard.hip): receivers on other shards get
+// their messages through one all-to-all (collective).
+void launch_lcc_push_sharded(Ctx& c, uint64_t* d_slot);
 void launch_compact_rows(Ctx& c, uint32_t stamp);
 void launch_count_state(Ctx& c, uint64_t* d_slot);
 void launch_compact_slist(Ctx& c);  // keeps the live entries of the last superstep's mask

@@ -1734,55 +1734,8 @@ __global__ __launch_bounds__(kBlock) void k_long_pack(LongList ll, uint32_t* __r
 //   verify: keep_bits(T_state, TN); survivors keep their flagged entries,
 //           flags cleared; an emptied vertex leaves S.
 // Rows are walked by one lane each (M rows are short after superstep 0).
-__device__ __forceinline__ int64_t m_find(const uint32_t* __restrict__ mcol, uint64_t b, uint32_t len,
-                                          const uint32_t* __restrict__ perm, uint32_t vid) {
-  uint64_t lo = b, hi = b + len;
-  while (lo < hi) {  // first entry whose neighbour id >= vid
-    const uint64_t mid = (lo + hi) >> 1;
-    if (perm[mcol[mid] & kPosMask] < vid) lo = mid + 1; else hi = mid;
-  }
-  return lo < b + len ? static_cast<int64_t>(lo) : -1;
-}
-
-// Entry-parallel: each wave takes 64 slist entries (rows); rows of at most kPushLong entries are walked
-// flattened over the wave (every lane takes every 64th entry of their concatenation, four in flight), longer
-// rows (R-MAT hubs: a lane walking a row of 10^5..10^6 entries, each with a binary search, took seconds) are
-// cut into kPushLong-entry pieces appended to a list that every wave of a second launch works through.
-static constexpr uint32_t kPushLong = 256;
-
-struct PushArgs {
-  const uint64_t* offp;
-  const uint32_t* slist;
-  const uint32_t* nS;
-  const uint16_t* tcur;
-  uint16_t* tnxt;
-  uint16_t* tst;
-  const uint32_t* perm;
-  uint32_t* mcol;
-  const uint32_t* mlen;
-  uint32_t* malive;
-  uint32_t* tn;
-  unsigned long long* pieces;   // (slist index << 32 | piece) of the long rows
-  unsigned long long* npieces;  // zeroed before the launches (the send and the verify have lists of their own)
-  uint64_t piece_cap;
-};
-
-// Sender entry: v (id vid, T_pub Tv) delivers to the neighbour in entry m.
-__device__ __forceinline__ void push_send_entry(const PushArgs& a, const uint16_t* s_adj, uint32_t v, uint32_t vid,
-                                                uint16_t Tv, uint32_t m) {
-  if (!(m & kAlive)) return;
-  const uint32_t u = m & kPosMask;
-  const uint16_t Tu = a.tcur[u];
-  if (!Tu || !(Tv & nbr_mask(Tu, s_adj))) return;  // u not in S, or not a valid parent
-  // (bits already present are not sent again: a hub's TN word takes one atomic per new bit instead of one per
-  // neighbour, which serialised on the word)
-  if ((a.tn[u] & Tv) != Tv) atomicOr(&a.tn[u], static_cast<uint32_t>(Tv));
-  const int64_t e = m_find(a.mcol, a.offp[u], a.mlen[u], a.perm, vid);
-  if (e >= 0) {
-    const uint32_t x = a.mcol[e];
-    if ((x & kPosMask) == v && (x & kAlive)) atomicOr(&a.mcol[e], kFlag);
-  }
-}
+// (m_find, PushArgs, push_send_entry and push_pieces live in pm_device.hpp: the sharded form in
+// pm_push_shard.hip shares them.)
 
 // Receiver-side verify of one entry of a surviving row: keep flagged entries (flags cleared); returns kept.
 __device__ __forceinline__ uint32_t push_verify_entry(uint32_t* mcol, uint64_t e) {
@@ -1791,18 +1744,6 @@ __device__ __forceinline__ uint32_t push_verify_entry(uint32_t* mcol, uint64_t e
   const bool keep = (m & kFlag) != 0;
   mcol[e] = (m & kPosMask) | (keep ? kAlive : 0u);
   return keep ? 1u : 0u;
-}
-
-// Appends the pieces of a long row (slist index i, len entries); false when the list is full.
-__device__ __forceinline__ bool push_pieces(const PushArgs& a, uint64_t i, uint32_t len) {
-  const uint32_t np = (len + kPushLong - 1) / kPushLong;
-  const unsigned long long b = atomicAdd(a.npieces, static_cast<unsigned long long>(np));
-  if (b + np > a.piece_cap) {  // full: the reserved slots below the cap are marked empty
-    for (uint64_t q = b; q < a.piece_cap && q < b + np; ++q) a.pieces[q] = ~0ull;
-    return false;
-  }
-  for (uint32_t q = 0; q < np; ++q) a.pieces[b + q] = (static_cast<unsigned long long>(i) << 32) | q;
-  return true;
 }
 
 // VERIFY = 0: the senders; 1: the receivers' verify (T from TN, survivors' entries compacted in place).
@@ -2288,9 +2229,11 @@ void build_tiling(Ctx& c) {
     const uint64_t first_nz = B[1], hi = B[kLB - 1];
     // every label-matching vertex sends along its out-edges: the scanned rows'
     // entries (other shards' rows are empty in offr); directed graphs scan
-    // in-rows, so the senders' out-degrees are summed instead
+    // in-rows, so the senders' out-degrees are summed instead (sharded: of the senders this shard owns -- the
+    // shards' sums are added)
     if (!c.symmetric)
-      for (uint64_t i = B[0]; i < hi; ++i) c.ss0_trav += c.deg_host[c.perm_host[i]];
+      for (uint64_t i = B[0]; i < hi; ++i)
+        if (c.nshards <= 1 || c.perm_host[i] % c.nshards == c.shard) c.ss0_trav += c.deg_host[c.perm_host[i]];
     if (hi <= first_nz) continue;
     if (c.symmetric) c.ss0_trav += dev_at(c.d_offr, hi) - dev_at(c.d_offr, first_nz);
     // kind k = [B[1+k], B[2+k]) for k < kHeavyKind (light class k); kHeavyKind = [B[1+kHeavyKind], hi)
@@ -2840,7 +2783,7 @@ size_t slist_scan_tmp_bytes(uint64_t words) {
   return tmp;
 }
 
-void launch_lcc_push(Ctx& c, uint64_t* d_slot) {
+void push_prepare(Ctx& c, PushArgs& a, PushArgs& av) {
   if (!c.d_tn) {
     PM_HIP_CHECK(hipMalloc(&c.d_tn, c.n * sizeof(uint32_t)));
     PM_HIP_CHECK(hipMemsetAsync(c.d_tn, 0, c.n * sizeof(uint32_t), c.stream));
@@ -2854,8 +2797,7 @@ void launch_lcc_push(Ctx& c, uint64_t* d_slot) {
     PM_HIP_CHECK(hipMalloc(&c.d_push, (2 * want + 2) * sizeof(unsigned long long)));
     c.push_cap = want;
   }
-  const uint32_t P = c.nranks <= 1 ? 1 : c.nranks;
-  PushArgs a{};
+  a = PushArgs{};
   a.offp = m_off(c);
   a.slist = c.d_slist;
   a.nS = c.d_nS;
@@ -2870,7 +2812,7 @@ void launch_lcc_push(Ctx& c, uint64_t* d_slot) {
   a.npieces = c.d_push;  // [0] the send's piece count, [1] the verify's
   a.pieces = c.d_push + 2;
   a.piece_cap = c.push_cap;
-  PushArgs av = a;
+  av = a;
   av.npieces = c.d_push + 1;
   av.pieces = c.d_push + 2 + c.push_cap;
   // no row of S longer than a piece (the last row compaction says so, c.push_long): no piece lists
@@ -2879,6 +2821,13 @@ void launch_lcc_push(Ctx& c, uint64_t* d_slot) {
   // without the piece launches a long row must be walked by its own wave: no capacity, so push_pieces always
   // reports the list full (should the no-long-row stamp ever be wrong, the row is still sent and verified)
   if (!pieces) a.piece_cap = av.piece_cap = 0;
+}
+
+void launch_lcc_push(Ctx& c, uint64_t* d_slot) {
+  PushArgs a, av;
+  push_prepare(c, a, av);
+  const bool pieces = c.push_long;
+  const uint32_t P = c.nranks <= 1 ? 1 : c.nranks;
   const unsigned grid = grid_for((uint64_t(c.nS_host) + kWave - 1) / kWave, kWpb, 16384);
   auto* trav = reinterpret_cast<unsigned long long*>(d_slot + 2 * P);
   const OwnerArgs oa = owner_args(c);
@@ -2887,6 +2836,15 @@ void launch_lcc_push(Ctx& c, uint64_t* d_slot) {
   if (pieces)
     hipLaunchKernelGGL(k_lcc_push_pieces<0>, dim3(kMaxGrid), dim3(kBlock), 0, c.stream, a, c.pa, oa,
                        partials(c, d_slot), uint64_t(0));
+  launch_push_verify(c, av, d_slot);
+}
+
+void launch_push_verify(Ctx& c, const PushArgs& av, uint64_t* d_slot) {
+  const bool pieces = c.push_long;
+  const uint32_t P = c.nranks <= 1 ? 1 : c.nranks;
+  const unsigned grid = grid_for((uint64_t(c.nS_host) + kWave - 1) / kWave, kWpb, 16384);
+  auto* trav = reinterpret_cast<unsigned long long*>(d_slot + 2 * P);
+  const OwnerArgs oa = owner_args(c);
   hipLaunchKernelGGL(k_lcc_push_rows<1>, dim3(grid), dim3(kBlock), 0, c.stream, av, c.pa, oa, partials(c, d_slot),
                      trav);
   if (pieces)

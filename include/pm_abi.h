@@ -135,15 +135,26 @@ typedef struct pm_run_stats {
   double comm_seconds;          /* host time inside the collectives of the search                        */
   uint64_t path_batches;        /* initiator batches of the exact-path path / cycle lines (one per line unless
                                    a line's tokens did not fit the device scratch arena at once)          */
+  /* A shard of a directed graph (symmetric = 0):                                                         */
+  uint64_t shard_in_entries;    /* entries of the in-rows of the owned vertices, built at construction    */
+  uint64_t shard_push_supersteps; /* push-form supersteps run sharded (before the replica hand-off)       */
+  uint64_t shard_push_messages; /* 12-byte messages this shard sent to other shards' receivers in them    */
 } pm_run_stats;
 
-/* One shard (rank) of a sharded search: the rows of ids v % nshards == shard. */
+/* One shard (rank) of a sharded search: the rows of ids v % nshards == shard; the row of a delegate
+ * (degree >= hub_threshold, nshards > 1) is split by target owner: a shard holds its entries u with
+ * u % nshards == shard.
+ * symmetric = 0 (a directed graph): off / col are the owned OUT-rows in the same shape (a delegate's
+ * out-row split by target owner) and degree holds the global OUT-degrees, which give the degree labels and the
+ * owner rule.  The in-rows superstep 0 scans are built on the devices when the contexts are created: every
+ * shard sends each out-entry (v -> u) to shard u % nshards, which sorts what it receives into the in-row CSR of
+ * the vertices it owns (rows in source-id order, duplicates and self loops kept).  Creation is collective. */
 typedef struct pm_shard_desc {
   uint64_t n;               /* global number of vertex ids                                   */
   const uint64_t* off;      /* n + 1 offsets by id: the owned rows, every other row empty    */
   const uint32_t* col;      /* off[n] targets of the owned rows, sorted within each row      */
   const uint32_t* degree;   /* n global degrees (degree labels, label-major order)           */
-  int32_t symmetric;
+  int32_t symmetric;        /* 1: every (u,v) has a matching (v,u); 0: directed, see above    */
   uint32_t nranks;          /* P used to name per-rank result files (owner rule)              */
   uint64_t hub_threshold;
   uint32_t nshards;         /* shards of the search (one per GPU / process)                  */

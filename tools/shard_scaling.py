@@ -10,6 +10,14 @@ checks the result directory against the oracle's fixture when one exists (result
 
     python3 tools/shard_scaling.py --config c5 --out gpurun_out/shards_c5.json     # S=27, hash-256, 4-cycle
     python3 tools/shard_scaling.py --config c4 --out gpurun_out/shards_c4.json     # S=28, degree, tree
+
+--directed SCALE P_GEN BACK: a directed graph instead (the generator's pairs u -> v, plus the reverse of every
+pair whose index % BACK == 0; tests/directed_inputs.py), built on the host and sharded by
+pm_run_beta_local_shards: per shard the in-row entries built at construction, the sharded push supersteps and
+their 12-byte messages, the replica at the hand-off and the sharded part's device time.  The shards share one
+chip, so the times are upper bounds of a shard's work, not a scaling curve.
+
+    python3 tools/shard_scaling.py --directed 22 8 2 --handoff 0 --out bench_out/shards_directed_h0.json
 """
 import argparse
 import json
@@ -22,6 +30,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 import fuzzypatternmatching_amd as pm  # noqa: E402
 import pmtest  # noqa: E402
@@ -35,7 +44,7 @@ CONFIGS = {
 KEYS = ("seconds", "device_seconds", "lcc_first_kernel_ms", "shard_sharded_ms", "nlcc_seconds", "split_lines",
         "line_overflows", "exact_lines", "shard_entries", "shard_rows", "shard_hub_entries", "shard_hubs_controlled",
         "shard_ss0_entries", "shard_ss0_survivors", "comm_calls", "comm_bytes", "comm_seconds", "replica_rows",
-        "replica_entries")
+        "replica_entries", "shard_in_entries", "shard_push_supersteps", "shard_push_messages")
 
 
 def main():
@@ -44,25 +53,40 @@ def main():
     ap.add_argument("--shards", type=int, nargs="+", default=[1, 2, 4, 8])
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--split-min", type=int, default=None, help="PM_SPLIT_LINES (first-position tokens)")
-    ap.add_argument("--handoff", type=int, default=None, help="PM_HANDOFF (superstep of the replica hand-off)")
+    ap.add_argument("--handoff", type=int, nargs="+", default=None,
+                    help="PM_HANDOFF (superstep of the replica hand-off); several: every shard count under each")
+    ap.add_argument("--directed", type=int, nargs=3, metavar=("SCALE", "P_GEN", "BACK"), default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.split_min is not None:
         os.environ["PM_SPLIT_LINES"] = str(args.split_min)
-    if args.handoff is not None:
-        os.environ["PM_HANDOFF"] = str(args.handoff)
+    handoffs = args.handoff or [None]
     scale, p_gen, pattern, lab, fixture = CONFIGS[args.config]
+    graph = None
+    if args.directed:
+        import directed_inputs
+        scale, p_gen, back = args.directed
+        fixture = None
+        off, col = directed_inputs.mixed(scale, p_gen, back)
+        graph = pm.Graph(off, col, False)
     pdir = os.path.join(ROOT, "patterns", pattern)
     labels = None if lab is None else pmtest.hash_labels(1 << scale, lab[0], salt=lab[1])
     fx = json.load(open(os.path.join(ROOT, "tests", "golden", fixture))) if fixture else None
-    out = {"config": args.config, "scale": scale, "p_gen": p_gen, "pattern": pattern,
+    out = {"config": args.config if graph is None else "directed mixed(%d, %d, %d)" % tuple(args.directed),
+           "scale": scale, "p_gen": p_gen, "pattern": pattern,
            "labels": "degree" if lab is None else f"hash32(v ^ {lab[1]}) % {lab[0]}", "repeats": args.repeats,
-           "split_min": os.environ.get("PM_SPLIT_LINES"), "handoff": os.environ.get("PM_HANDOFF"), "runs": {}}
-    for n in args.shards:
+           "split_min": os.environ.get("PM_SPLIT_LINES"), "handoff": args.handoff, "runs": {}}
+    for h, n in [(h, n) for h in handoffs for n in args.shards]:
+        if h is not None:
+            os.environ["PM_HANDOFF"] = str(h)
         td = tempfile.mkdtemp(prefix="pmshards")
         t0 = time.time()
-        each = pm.run_rmat_local_shards_each(scale, p_gen, pdir, n, td, max_iterations=64, labels=labels,
-                                             repeats=args.repeats)
+        if graph is None:
+            each = pm.run_rmat_local_shards_each(scale, p_gen, pdir, n, td, max_iterations=64, labels=labels,
+                                                 repeats=args.repeats)
+        else:
+            each = pm.run_beta_local_shards_each(graph, pdir, n, td, max_iterations=64, labels=labels,
+                                                 repeats=args.repeats)
         wall = time.time() - t0
         run = {"wall_s_incl_generation": round(wall, 2), "per_shard": {k: [s[k] for s in each] for k in KEYS},
                "result": {k: each[0][k] for k in ("iterations", "lcc_edges", "nlcc_edges", "tds_edges", "walks",
@@ -78,11 +102,18 @@ def main():
             run["fixture_diffs"] = diffs[:4]
         shutil.rmtree(td, ignore_errors=True)
         ps = run["per_shard"]
-        print(f"N={n}: lcc_first max {max(ps['lcc_first_kernel_ms']):.3f} ms, sharded part max "
+        print(f"N={n}{'' if h is None else f' PM_HANDOFF={h}'}: lcc_first max {max(ps['lcc_first_kernel_ms']):.3f} ms, sharded part max "
               f"{max(ps['shard_sharded_ms']):.3f} ms, lines max {max(ps['nlcc_seconds']) * 1e3:.3f} ms "
               f"(split {ps['split_lines'][0]}), device {max(ps['device_seconds']) * 1e3:.3f} ms, "
               f"fixture {run.get('fixture_match')}", file=sys.stderr, flush=True)
-        out["runs"][str(n)] = run
+        if graph is not None:
+            ie, k = ps["shard_in_entries"], max(1, ps["shard_push_supersteps"][0])
+            print(f"     in-row entries max {max(ie)} mean {sum(ie) / len(ie):.0f}; sharded push supersteps "
+                  f"{ps['shard_push_supersteps'][0]}, messages {sum(ps['shard_push_messages'])} "
+                  f"({12 * sum(ps['shard_push_messages']) / k:.0f} B per superstep); replica rows "
+                  f"{ps['replica_rows'][0]}, final vertices {run['result']['final_vertices']}",
+                  file=sys.stderr, flush=True)
+        out["runs"][str(n) if len(handoffs) == 1 else f"{n}@handoff{h}"] = run
     s = json.dumps(out)
     if args.out:
         with open(args.out, "w") as f:
